@@ -57,6 +57,32 @@ def cached_problem(scale):
     return prob
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much in all (a larger output is dumped as a fixed, seeded row sample)
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: array} as out_dir/<name>.npy in float64.  If they exceed DUMP_LIMIT_BYTES together, the arrays are grouped by
+    row count and every group of 1 MiB or more keeps one fixed, seeded sample of its rows (seed 0, sorted), the same rows in
+    each of its arrays (ids stay next to their values); smaller groups are written whole.  Two runs stay comparable row for row."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    groups = {}
+    for k, v in arrays.items():
+        groups.setdefault(len(v) if v.ndim else 0, []).append(k)
+    size = lambda ks: sum(arrays[k].nbytes for k in ks)  # noqa: E731
+    big = {n: ks for n, ks in groups.items() if n > 1 and size(ks) >= 1 << 20}
+    big_bytes = sum(size(ks) for ks in big.values())
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        frac = (DUMP_LIMIT_BYTES - 4096 * len(arrays) - (total - big_bytes)) / float(big_bytes)   # (4 KiB per .npy header)
+        for n, ks in big.items():
+            rows = np.sort(np.random.default_rng(0).choice(n, max(1, int(n * frac)), replace=False))
+            for k in ks:
+                arrays[k] = arrays[k][rows]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 LM_BLOCK = 10   # Cg2oOptimizer::_optimizeUnLimited runs optimize(10) blocks (Cg2oOptimizer.cpp:975)
 
 
@@ -494,7 +520,12 @@ def main():
     ap.add_argument("--hook", choices=("native", "torch"), default="native",
                     help="N > 1: the all-reduce of the reduced system through the library's own RCCL communicator (C++, svi_rccl_*) or "
                          "through torch.distributed (the gloo rehearsal always uses torch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed LM run computed in its last step (optimised poses and "
+                         "landmarks with their ids, final chi2) as DIR/<name>.npy in float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     import torch
     import torch.distributed as dist
@@ -549,8 +580,9 @@ def main():
             else:
                 ba.set_allreduce(sdist.make_allreduce_hook())
 
-    def measure(prob, steps, warmup):
-        """one handle per rank over `prob` (landmark-sharded `world` ways), W untimed + K timed LM iterations"""
+    def measure(prob, steps, warmup, dump_dir=None):
+        """one handle per rank over `prob` (landmark-sharded `world` ways), W untimed + K timed LM iterations;
+        dump_dir: rank 0 writes the estimates after the last timed iteration there (dump_outputs)"""
         cam = prob["cam"]
         ba = svi.BundleAdjuster(cam["fx"], cam["fy"], cam["cx"], cam["cy"], cam["baseline_m"], device=local, rank=rank, n_ranks=world,
                                 chol_tile=args.chol_tile)
@@ -576,6 +608,12 @@ def main():
         t1 = time.perf_counter()
         ba.sync_host()
         readback_ms = 1e3 * (time.perf_counter() - t1)
+        if dump_dir is not None:   # (every rank reads back alike: with several ranks the getters may be collective)
+            pose_ids, poses = ba.get_poses()
+            lm_ids, landmarks = ba.get_landmarks()
+            if rank == 0:
+                dump_outputs(dump_dir, {"poses": poses, "pose_ids": pose_ids, "landmarks": landmarks, "landmark_ids": lm_ids,
+                                        "chi2": np.array(chi)})
         ba.close()
         return dict(dt=dt, stats=s1, trials=trials, chi=chi, readback_ms=readback_ms, stored=stored)
 
@@ -583,7 +621,7 @@ def main():
     scale_of = {"weak": world, "strong": 1}
     prob = cached_problem(scale_of[args.scaling])
     cam = prob["cam"]
-    head = measure(prob, args.steps, args.warmup)
+    head = measure(prob, args.steps, args.warmup, dump_dir=args.dump_outputs)
     dt, stored = head["dt"], head["stored"]
     units = world if args.scaling == "weak" else 1     # weak: shard-iterations per second over the whole job
     other = None

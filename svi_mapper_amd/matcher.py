@@ -44,6 +44,7 @@ class HammingMatcher:
 
     def __init__(self, device=0, stream=None):
         self._lib = _capi.load_library()
+        self._children = {}   # handles created on this one (tracker, BRIEF): their destroy reads the matcher's device and stream
         h = C.c_void_p()
         check(self._lib.svi_matcher_create(int(device), C.c_void_p(stream) if stream else None, C.byref(h)),
               "svi_matcher_create")
@@ -52,8 +53,21 @@ class HammingMatcher:
 
     def close(self):
         if getattr(self, "_h", None):
+            for destroy, h in list(self._children.values()):   # before the matcher itself, whichever object is finalised first
+                destroy(h)
+            self._children.clear()
             self._lib.svi_matcher_destroy(self._h)
             self._h = None
+
+    def _adopt(self, h, destroy):
+        """h: a handle created on this matcher; destroy(h) runs in _release(h), or in close() if the matcher goes first (a garbage
+        cycle finalises its objects in no particular order)"""
+        self._children[h.value] = (destroy, h)
+
+    def _release(self, h):
+        entry = self._children.pop(h.value, None)
+        if entry is not None:
+            entry[0](entry[1])
 
     def __del__(self):
         try:

@@ -136,6 +136,7 @@ class FundamentalMatcher:
         h = C.c_void_p()
         check(self._lib.svi_tracker_create(self._h, C.byref(self._cam), C.byref(h)), "svi_tracker_create")
         self._trk = h
+        self.matcher._adopt(h, self._lib.svi_tracker_destroy)
         self._bound = (None, None)   # the (extractor, detector) the tracker handle is bound to, with their ctypes thunks kept alive
         self._thunks = ()
         self._frame = None           # tensors of the planned frame (kept alive while the tracker holds their pointers)
@@ -143,7 +144,7 @@ class FundamentalMatcher:
 
     def close(self):
         if getattr(self, "_trk", None):
-            self._lib.svi_tracker_destroy(self._trk)
+            self.matcher._release(self._trk)
             self._trk = None
 
     def __del__(self):
@@ -532,13 +533,14 @@ class BriefExtractor:
         h = C.c_void_p()
         check(self._lib.svi_brief_create(self.matcher._h, pat.ctypes.data_as(C.c_void_p), C.byref(h)), "svi_brief_create")
         self._h = h
+        self.matcher._adopt(h, self._lib.svi_brief_destroy)
         self.device = torch.device("cuda", device)
         self._ext = torch.cuda.ExternalStream(self.matcher.stream, device=self.device)
         self._shape = [None, None]
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.svi_brief_destroy(self._h)
+            self.matcher._release(self._h)
             self._h = None
 
     def __del__(self):
