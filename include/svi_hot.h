@@ -705,6 +705,16 @@ int svi_ba_debug_aux_jacobians(svi_ba* ba, double* se3_err /*n_se3 x 6*/, double
  * S (n x n row-major, full symmetric) and g (n), n = 6 * free poses; *n_out receives n */
 int svi_ba_debug_reduced_system(svi_ba* ba, double lambda, double* S, double* g, int64_t cap,
                                 int64_t* n_out);
+/* the production solve of that system: reduces as svi_ba_debug_reduced_system does, then runs the tile Cholesky and the
+ * backward substitution a trial runs (same plan, same path selection) and copies dx (n, natural free-pose order; S dx = g).
+ * *status: 0, k+1 for a failed pivot, -1 for a landmark block that is not positive definite (dx then holds nothing
+ * meaningful), -3 for a hand-over time-out of the one-launch backward substitution.  *kernels: SVI_SOLVE_K_* bits of the solve kernels that ran.  Any lambda is accepted; the estimates
+ * are untouched */
+#define SVI_SOLVE_K_ALL   1 /* k_back_solve_all: one-launch backward substitution (tile 48) */
+#define SVI_SOLVE_K_INL   2 /* k_back_solve_inl: per level, column lists inline (tile 48) */
+#define SVI_SOLVE_K_LEVEL 4 /* k_back_solve: per level */
+#define SVI_SOLVE_K_TRSM  8 /* k_trsm: the off-diagonal solve of tile 96 (folded into the diagonal kernel at tile 48) */
+int svi_ba_debug_solve(svi_ba* ba, double lambda, double* dx, int64_t cap, int64_t* n_out, int* status, int* kernels);
 
 /* mean duration (ms) of the Jacobian sweep kernel over `reps` back-to-back launches on the handle's stream,
  * bracketed by two HIP events (the state is not modified: the sweep only writes linearisation outputs) */

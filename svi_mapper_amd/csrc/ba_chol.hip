@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "ba_device.h"
+#include "svi_hot.h"
 #include "ba_math.h"
 
 namespace svi {
@@ -1344,9 +1345,11 @@ __global__ __launch_bounds__(kPotrfThreads) void k_back_solve_all(const SolveRec
 }
 
 // levels [st_begin, st_end) of the factorisation, then (solve) the backward substitution
+// kernels (optional): ORed with the SVI_SOLVE_K_* bits of the solve kernels this call launched (svi_hot.h)
 template <int TS>
 int run(const CholPlan& p, double* S, double* Lt, double* Linv, double* g, double* x, double lambda, int n, int* status, hipStream_t s,
-        const PoseTail* tail, int* tail_done, int st_begin, int st_end, bool solve, double* Su = nullptr, double* gu = nullptr)
+        const PoseTail* tail, int* tail_done, int st_begin, int st_end, bool solve, double* Su = nullptr, double* gu = nullptr,
+        int* kernels = nullptr)
 {
     const bool split = TS == 48 && Su != nullptr;
     if (tail_done) *tail_done = 0;
@@ -1383,7 +1386,10 @@ int run(const CholPlan& p, double* S, double* Lt, double* Linv, double* g, doubl
         if (split) hipLaunchKernelGGL((k_potrf_inv<TS, TS == 48>), dim3(nc + ntg * Q * Q), dim3(kPotrfThreads), lds_p, s, S, Lt, Linv, g, yv, n, lambda, status, 0, sa, x, Su, gu);
         else hipLaunchKernelGGL((k_potrf_inv<TS, false>), dim3(nc + ntg * Q * Q), dim3(kPotrfThreads), lds_p, s, S, Lt, Linv, g, yv, n, lambda, status, 0, sa, x, nullptr, nullptr);
         const int i0 = p.h_trsm_ptr[st], ni = p.h_trsm_ptr[st + 1] - i0;
-        if (ni > 0 && !Fold<TS>::on) hipLaunchKernelGGL(k_trsm<TS>, dim3(ni * QT * QT), dim3(kBlock), lds_g, s, S, Lt, Linv, p.st_tile + i0, p.st_col + i0, status);
+        if (ni > 0 && !Fold<TS>::on) {
+            hipLaunchKernelGGL(k_trsm<TS>, dim3(ni * QT * QT), dim3(kBlock), lds_g, s, S, Lt, Linv, p.st_tile + i0, p.st_col + i0, status);
+            if (kernels) *kernels |= SVI_SOLVE_K_TRSM;
+        }
     }
 #ifdef POTRF_TS
     {
@@ -1409,6 +1415,7 @@ int run(const CholPlan& p, double* S, double* Lt, double* Linv, double* g, doubl
             if (tail) { pt = *tail; if (tail_done) *tail_done = 1; }
             hipLaunchKernelGGL(k_back_solve_all<TS>, dim3(p.n_solve_cols + (tail ? 1 : 0)), dim3(kPotrfThreads), 0, s, p.solve_recs, Lt, Linv, yv, x, status, pt,
                                g_backsolve_spin_limit.load(std::memory_order_relaxed), defer_y);
+            if (kernels) *kernels |= SVI_SOLVE_K_ALL;
             return 0;
         }
     }
@@ -1417,10 +1424,12 @@ int run(const CholPlan& p, double* S, double* Lt, double* Linv, double* g, doubl
         if constexpr (TS == 48) {
             if (p.h_solve_inl && p.h_solve_inl[st].n == nc) {
                 hipLaunchKernelGGL(k_back_solve_inl<TS>, dim3(nc), dim3(kPotrfThreads), 0, s, p.h_solve_inl[st], Lt, Linv, x, status);
+                if (kernels) *kernels |= SVI_SOLVE_K_INL;
                 continue;
             }
         }
         hipLaunchKernelGGL(k_back_solve<TS>, dim3(nc), dim3(kPotrfThreads), 0, s, Lt, Linv, x, p, reinterpret_cast<const int4*>(p.step_desc) + 2 * c0, status);
+        if (kernels) *kernels |= SVI_SOLVE_K_LEVEL;
     }
     return 0;
 }
@@ -1487,12 +1496,13 @@ int chol_factor_solve(const CholPlan& p, double* S, double* Lt, double* Linv, do
 
 // the same in pieces: levels [st_begin, st_end) only; the backward substitution (and the trial poses) behind the last piece
 // Su / gu (tile 48, optional): the updates go to these arrays instead of into S / g (see potrf_sweep_mfma)
+// kernels (optional): ORed with the SVI_SOLVE_K_* bits of the solve kernels launched
 int chol_factor_range(const CholPlan& p, double* S, double* Lt, double* Linv, double* g, double* x, double lambda, int n, int* status,
-                      void* st, const PoseTail* tail, int* tail_done, int st_begin, int st_end, int solve, double* Su, double* gu)
+                      void* st, const PoseTail* tail, int* tail_done, int st_begin, int st_end, int solve, double* Su, double* gu, int* kernels)
 {
     hipStream_t s = static_cast<hipStream_t>(st);
-    return p.TS == 48 ? run<48>(p, S, Lt, Linv, g, x, lambda, n, status, s, tail, tail_done, st_begin, st_end, solve != 0, Su, gu)
-                      : run<96>(p, S, Lt, Linv, g, x, lambda, n, status, s, tail, tail_done, st_begin, st_end, solve != 0);
+    return p.TS == 48 ? run<48>(p, S, Lt, Linv, g, x, lambda, n, status, s, tail, tail_done, st_begin, st_end, solve != 0, Su, gu, kernels)
+                      : run<96>(p, S, Lt, Linv, g, x, lambda, n, status, s, tail, tail_done, st_begin, st_end, solve != 0, nullptr, nullptr, kernels);
 }
 
 } // namespace svi

@@ -52,7 +52,8 @@ int chol_factor_solve(const CholPlan& p, double* S, double* Lt, double* Linv, do
 // svi_debug_set_backsolve_spin_limit: the tests shrink it to provoke the time-out path)
 std::atomic<int> g_backsolve_spin_limit{1 << 22};
 int chol_factor_range(const CholPlan& p, double* S, double* Lt, double* Linv, double* g, double* x, double lambda, int n, int* status,
-                      void* st, const PoseTail* tail, int* tail_done, int st_begin, int st_end, int solve, double* Su, double* gu);
+                      void* st, const PoseTail* tail, int* tail_done, int st_begin, int st_end, int solve, double* Su, double* gu,
+                      int* kernels = nullptr);
 int build_structure(svi_ba* ba); // ba_structure.cpp
 int reupload_state(svi_ba* ba);
 
@@ -1219,6 +1220,23 @@ int svi_ba_debug_time_sweep_part(svi_ba* ba, int reps, int which, double* ms_avg
     return time_sweep_impl(ba, reps, which, ms_avg);
 }
 
+// the debug taps' reduction: linearise at the current estimate, reduce with damping lambda into the tiles of d.S / d.g
+// (lambda not on the diagonal yet: the factorisation adds it), all ranks summed
+static int debug_reduce(svi_ba* ba, double lambda)
+{
+    BaDev& d = ba->d;
+    ba->spec_lin_state = -1; // (a block that ended on a rejected speculated trial leaves the buffers of ANOTHER state's sweep behind)
+    SVI_TRY(linearize(ba));
+    SVI_HIP(hipMemsetAsync(d.chol_status, 0, sizeof(int), ba->stream));
+    set_assembly_flags(ba);
+    SVI_TRY(zero_reduced_system(ba));
+    ba_invert_landmarks(d, lambda, ba->stream);
+    ba_schur(d, nullptr, ++ba->stage_seq, 0, 0, ba->stream);
+    assemble(ba);
+    SVI_HIP(hipGetLastError());
+    return allreduce(ba, d.g, (size_t)d.red_count);
+}
+
 // linearise at the current estimate, reduce with damping lambda, return dense S (with lambda on its
 // diagonal) and g
 int svi_ba_debug_reduced_system(svi_ba* ba, double lambda, double* S, double* g, int64_t cap, int64_t* n_out)
@@ -1230,16 +1248,7 @@ int svi_ba_debug_reduced_system(svi_ba* ba, double lambda, double* S, double* g,
     const int64_t n = 6 * (int64_t)d.Pf;
     *n_out = n;
     if (cap < n) return fail(SVI_ERR_INVALID, "capacity %lld < n %lld", (long long)cap, (long long)n);
-    ba->spec_lin_state = -1; // (a block that ended on a rejected speculated trial leaves the buffers of ANOTHER state's sweep behind)
-    SVI_TRY(linearize(ba));
-    SVI_HIP(hipMemsetAsync(d.chol_status, 0, sizeof(int), ba->stream));
-    set_assembly_flags(ba);
-    SVI_TRY(zero_reduced_system(ba));
-    ba_invert_landmarks(d, lambda, ba->stream);
-    ba_schur(d, nullptr, ++ba->stage_seq, 0, 0, ba->stream);
-    assemble(ba);
-    SVI_HIP(hipGetLastError());
-    SVI_TRY(allreduce(ba, d.g, (size_t)d.red_count));
+    SVI_TRY(debug_reduce(ba, lambda));
     const int TS = d.TS, NT = d.NT;
     std::vector<double> tiles((size_t)d.n_tiles * TS * TS), gv((size_t)NT * TS);
     std::vector<int> tmap((size_t)NT * NT);
@@ -1266,6 +1275,37 @@ int svi_ba_debug_reduced_system(svi_ba* ba, double lambda, double* S, double* g,
                 }
         }
     for (int64_t i = 0; i < n; ++i) { S[nat[i] * n + nat[i]] += lambda; g[nat[i]] = gv[i]; }
+    return SVI_OK;
+}
+
+// the reduced system of svi_ba_debug_reduced_system solved by the production factorisation + backward substitution (no pose
+// tail: the estimates stay as they are); dx back in natural free-pose order
+int svi_ba_debug_solve(svi_ba* ba, double lambda, double* dx, int64_t cap, int64_t* n_out, int* status, int* kernels)
+{
+    if (!ba || !dx || !n_out || !status || !kernels) return fail(SVI_ERR_INVALID, "null argument");
+    if (!ba->initialized) return fail(SVI_ERR_STATE, "debug tap before svi_ba_initialize");
+    SVI_HIP(svi::enter_device(ba->opt.device));
+    BaDev& d = ba->d;
+    const int64_t n = 6 * (int64_t)d.Pf;
+    *n_out = n;
+    *status = 0;
+    *kernels = 0;
+    if (cap < n) return fail(SVI_ERR_INVALID, "capacity %lld < n %lld", (long long)cap, (long long)n);
+    SVI_TRY(debug_reduce(ba, lambda));
+    if (d.NT == 0) return SVI_OK;
+    if (chol_factor_range(ba->plan, d.S, d.Lt, d.Linv, d.g, d.dx, lambda, (int)n, d.chol_status, ba->stream, nullptr, nullptr, 0,
+                          ba->plan.n_steps, 1, nullptr, nullptr, kernels) != 0)
+        return fail(SVI_ERR_HIP, "Cholesky kernels could not be configured (LDS request refused)");
+    SVI_HIP(hipGetLastError());
+    std::vector<double> x((size_t)n);
+    int st = 0;
+    SVI_HIP(hipMemcpyAsync(x.data(), d.dx, sizeof(double) * n, hipMemcpyDeviceToHost, ba->stream));
+    SVI_HIP(hipMemcpyAsync(&st, d.chol_status, sizeof(int), hipMemcpyDeviceToHost, ba->stream));
+    SVI_HIP(hipMemsetAsync(d.chol_status, 0, sizeof(int), ba->stream)); // read here: clean for the next trial
+    SVI_HIP(hipStreamSynchronize(ba->stream));
+    *status = st;
+    for (int64_t a = 0; a < (int64_t)d.Pf; ++a)
+        for (int c = 0; c < 6; ++c) dx[6 * a + c] = x[(size_t)(6 * (int64_t)ba->red_perm[a] + c)];
     return SVI_OK;
 }
 

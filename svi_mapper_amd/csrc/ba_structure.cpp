@@ -236,19 +236,22 @@ void pose_coupling(Build& b)
     // entered once is skipped (bit (last - first) of seen[first]; longer or broken runs are always entered).
     std::vector<uint64_t> seen(b.use_cpl ? (size_t)Pf : 0, 0);
     for (int l = 0; l < b.Ltot; ++l) {
-        int k0 = b.g_ptr[l];
-        const int k1 = b.g_ptr[l + 1];
-        while (k0 < k1 && b.pose_red[b.g_pose[k0]] < 0) ++k0; // (fixed poses have the lowest slots: their edges come first)
+        int k0 = b.g_ptr[l], k1 = b.g_ptr[l + 1];
+        // edges to fixed poses (no reduced index) sit wherever their slots do - fixed poses may interleave with free ones:
+        // trimmed from both ends here, skipped inside the range below
+        while (k0 < k1 && b.pose_red[b.g_pose[k0]] < 0) ++k0;
+        while (k1 > k0 && b.pose_red[b.g_pose[k1 - 1]] < 0) --k1;
         if (k0 == k1) continue;
         const int first = b.pose_red[b.g_pose[k0]], len = b.pose_red[b.g_pose[k1 - 1]] - first;
-        const bool run = len + 1 == k1 - k0 && len < 64; // as many edges as poses between the first and the last: consecutive
+        const bool run = len + 1 == k1 - k0 && len < 64; // as many edges as free poses between the first and the last: consecutive
+                                                         // (an edge to a fixed pose inside the range makes it count as broken)
         if (b.use_cpl && run && (seen[first] >> len & 1) && len <= b.span) continue; // (first and last edge only: the common case)
         if (ba->lms[ba->lm_order[l]].fixed) continue;
         b.span = std::max(b.span, len);
         if (!b.use_cpl) continue;
         if (run) seen[first] |= (uint64_t)1 << len;
         reds.clear();
-        for (int k = k0; k < k1; ++k) reds.push_back(b.pose_red[b.g_pose[k]]);
+        for (int k = k0; k < k1; ++k) if (b.pose_red[b.g_pose[k]] >= 0) reds.push_back(b.pose_red[b.g_pose[k]]);
         for (size_t x = 0; x < reds.size(); ++x) {
             uint8_t* row = &b.cpl[(size_t)reds[x] * Pf];
             for (size_t y = 0; y <= x; ++y) row[reds[y]] = 1;

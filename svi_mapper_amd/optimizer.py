@@ -319,3 +319,18 @@ class BundleAdjuster:
         check(self._lib.svi_ba_debug_reduced_system(self._h, float(lam), _p(S, f64p), _p(g, f64p), n, C.byref(nn)),
               "svi_ba_debug_reduced_system")
         return S, g
+
+    # bits of debug_solve's `kernels` (svi_hot.h SVI_SOLVE_K_*)
+    SOLVE_K_ALL, SOLVE_K_INL, SOLVE_K_LEVEL, SOLVE_K_TRSM = 1, 2, 4, 8
+
+    def debug_solve(self, lam):
+        """(dx, status, kernels): reduced_system(lam) solved by the production tile Cholesky; dx in natural free-pose order,
+        status 0 / k+1 (failed pivot: dx meaningless) / -3, kernels the SOLVE_K_* bits of the solve kernels that ran"""
+        n = 6 * self.stats().n_poses_free
+        dx = np.zeros(n)
+        nn = C.c_int64(0)
+        st = C.c_int(0)
+        k = C.c_int(0)
+        check(self._lib.svi_ba_debug_solve(self._h, float(lam), _p(dx, f64p), n, C.byref(nn), C.byref(st), C.byref(k)),
+              "svi_ba_debug_solve")
+        return dx, st.value, k.value

@@ -57,21 +57,35 @@ def test_initial_chi2(svi, oracle, small):
     assert abs(pg - po) <= 1e-10 * po and abs(rg - ro) <= 1e-10 * ro
 
 
-@pytest.mark.parametrize("tile", [48, 96])
-def test_reduced_system_is_schur_of_oracle_H(svi, oracle, small, tile):
-    g, _ = _make(svi.BundleAdjuster, small, chol_tile=tile)
-    o, _ = _make(oracle.OracleBA, small)
+def _schur_graph(name, cls, small, **kw):
+    """the graphs of test_reduced_system_is_schur_of_oracle_H, each at most ~8000 unknowns (the oracle's H is dense)"""
+    import ba_graphs as bg
+    if name == "small":
+        return bg.make(cls, small, **kw)
+    if name == "loop_closure":
+        return bg.loop_closure(cls, synth.make_ba_problem(90, 2200, 18000, seed=13), **kw)
+    if name == "interleaved_fixed":
+        return bg.interleaved_fixed(cls, synth.make_ba_problem(80, 2000, 15000, seed=41), every=5, **kw)
+    if name == "vi":
+        return bg.make(cls, synth.make_vi_problem(40, 2000, 14000), **kw)
+    assert name == "120_poses"
+    return bg.make(cls, synth.make_ba_problem(120, 2000, 16000, seed=5), **kw)
+
+
+@pytest.mark.parametrize("graph,tile,order", [("small", 48, 0), ("small", 96, 0), ("loop_closure", 48, 0), ("loop_closure", 96, 1),
+                                              ("interleaved_fixed", 48, 0), ("interleaved_fixed", 96, 0), ("vi", 48, 0),
+                                              ("120_poses", 48, 0), ("120_poses", 48, 1), ("120_poses", 96, 0), ("120_poses", 96, 1)])
+def test_reduced_system_is_schur_of_oracle_H(svi, oracle, small, graph, tile, order):
+    """the reduced camera system of the tap against the Schur complement of the oracle's dense H: the 12-pose graph, fill
+    from loop closures, fixed poses between free ones, odometry and gravity edges with real measurements, 120 poses"""
+    import ba_graphs as bg
+    g = _schur_graph(graph, svi.BundleAdjuster, small, chol_tile=tile, chol_order=order)
+    o = _schur_graph(graph, oracle.OracleBA, small)
     g.initialize()
     o.initialize()
     lam = 3.7
     S, gv = g.reduced_system(lam)
-    H, b, pc, lc = o.dense_system()
-    n = len(b)
-    H = H + lam * np.eye(n)
-    nl = 3 * (lc >= 0).sum()
-    Hll, Hpl, Hpp = H[:nl, :nl], H[nl:, :nl], H[nl:, nl:]
-    Sref = Hpp - Hpl @ np.linalg.solve(Hll, Hpl.T)
-    gref = b[nl:] - Hpl @ np.linalg.solve(Hll, b[:nl])
+    Sref, gref = bg.oracle_schur(o, lam)
     assert S.shape == Sref.shape
     scale = np.abs(Sref).max()
     assert np.abs(S - Sref).max() <= 1e-10 * scale

@@ -10,9 +10,11 @@ from svi_mapper_amd import synth
 pytestmark = pytest.mark.gpu
 
 
-def _run_sharded(svi, prob, n_ranks, iters, extra=None, make=None, until=False):
+def _run_sharded(svi, prob, n_ranks, iters, extra=None, make=None, until=False, tap=None):
     """n_ranks handles in n_ranks threads of one process; the hook sums their buffers in a fixed order.
-    make(rank, n_ranks) (optional) builds the handle with its graph instead of synth.build_ba_graph(prob)."""
+    make(rank, n_ranks) (optional) builds the handle with its graph instead of synth.build_ba_graph(prob).
+    tap(ba) (optional) runs on every rank right after initialize(); its result ends the rank's tuple:
+    (done, poses, landmarks, chi2, n_landmarks_local, lm_trials, chol_failures, lambdas, n_edges_proj_local, tap result)."""
     import torch
     cam = prob["cam"] if prob is not None else None
     barrier = threading.Barrier(n_ranks)
@@ -50,6 +52,7 @@ def _run_sharded(svi, prob, n_ranks, iters, extra=None, make=None, until=False):
                 extra(ba)
             ba.set_allreduce(hook_for(rank))
             ba.initialize()
+            tapped = tap(ba) if tap is not None else None
             done, lams = [], []
             if until:   # the whole _optimizeUnLimited schedule (every block's lambda_0 exchange included)
                 done = list(ba.optimize_until())
@@ -59,7 +62,7 @@ def _run_sharded(svi, prob, n_ranks, iters, extra=None, make=None, until=False):
                 lams.append(ba.lm_lambda)
             st = ba.stats()
             out[rank] = (done, ba.get_poses()[1], ba.get_landmarks()[1], ba.chi2(), st.n_landmarks_local, st.lm_trials, st.chol_failures,
-                         lams)
+                         lams, st.n_edges_proj_local, tapped)
             ba.close()
         except Exception as e:  # noqa: BLE001
             errs.append(e)
@@ -137,6 +140,13 @@ def test_c4_eight_shards_equal_unsharded(svi):
     out = _run_sharded(svi, prob, 8, iters)
     loc = [o[4] for o in out]
     assert sum(loc) == prob["n_lm"] and min(loc) > 0 and max(loc) < 1.6 * min(loc)   # (shards are balanced by EDGE count, not landmarks)
+    # the rule of local_edges (ba_structure.cpp): a shard boundary is the first landmark whose edges reach rank * E / n_ranks, so
+    # every shard's edge count is within one landmark's degree of E / n_ranks (the degree is bounded by the observations
+    # synth drew for the landmark: admission only drops edges)
+    e_loc = [o[8] for o in out]
+    deg = int(np.bincount(prob["obs_lm"]).max())
+    assert sum(e_loc) == st.n_edges_proj
+    assert all(abs(e - st.n_edges_proj / 8) <= deg for e in e_loc), (e_loc, st.n_edges_proj, deg)
     for o in out:
         assert o[0] == done and o[5] == st.lm_trials and o[6] == 0
         assert o[7] == out[0][7]                                  # the same damping on every rank, bit for bit
@@ -356,3 +366,22 @@ def test_dlpack_alias_on_device(svi):
         t[2, 3] = 5
         assert src[2, 3].item() == 5
     assert _dlpack.alias(0, (0, 4), torch.float32, torch.device("cuda", 0)).shape == (0, 4)
+
+
+def test_sharded_reduced_system_is_schur_of_oracle_H(svi, oracle):
+    """three landmark shards: the reduced system every rank holds after the all-reduce is the Schur complement of the
+    unsharded oracle's H (the same 1e-10 as the single handle)"""
+    import ba_graphs as bg
+    prob = synth.make_ba_problem(30, 2000, 15000, seed=23)
+    lam = 3.7
+    o = bg.make(oracle.OracleBA, prob)
+    o.initialize()
+    Sref, gref = bg.oracle_schur(o, lam)
+    out = _run_sharded(svi, prob, 3, (), tap=lambda ba: ba.reduced_system(lam))
+    assert min(x[4] for x in out) > 0
+    for x in out:
+        S, g = x[9]
+        assert S.shape == Sref.shape
+        assert np.abs(S - Sref).max() <= 1e-10 * np.abs(Sref).max()
+        assert np.abs(g - gref).max() <= 1e-10 * np.abs(gref).max()
+        assert np.array_equal(S, out[0][9][0]) and np.array_equal(g, out[0][9][1])

@@ -23,5 +23,5 @@ void ba_gather_edges(const double*, const uint8_t*, const int*, const int*, int,
 void ba_configure_kernels(int) {}
 int chol_potrf_probe(int, int, int, double*) { return 0; }
 int chol_factor_solve(const CholPlan&, double*, double*, double*, double*, double*, double, int, int*, void*, const PoseTail*, int* done) { if (done) *done = 0; return 0; }
-int chol_factor_range(const CholPlan&, double*, double*, double*, double*, double*, double, int, int*, void*, const PoseTail*, int* done, int, int, int, double*, double*) { if (done) *done = 0; return 0; }
+int chol_factor_range(const CholPlan&, double*, double*, double*, double*, double*, double, int, int*, void*, const PoseTail*, int* done, int, int, int, double*, double*, int*) { if (done) *done = 0; return 0; }
 } // namespace svi

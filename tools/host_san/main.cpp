@@ -1,7 +1,8 @@
 // main.cpp — drives the host side of the BA C ABI (include/svi_hot.h) under AddressSanitizer + UBSan without a GPU:
 // random trajectory graphs through the reference-shaped construction calls, svi_ba_initialize (the whole structure
 // analysis: vertex order, nested dissection, edge sorting, tile structure, Schur work lists, every upload size) for 1, 2
-// and 3 ranks and both tile sizes / elimination orders, the .g2o writer and reader, pruning and the write-back.
+// and 3 ranks and both tile sizes / elimination orders, fixed poses between free ones, the .g2o writer and reader, pruning
+// and the write-back.
 // The LM loop itself needs the kernels and is not run here (tests/test_ba_gpu.py does that on the GPU).
 // usage: host_san [n_graphs] [seed] ; prints one line per graph and "host_san: ok"
 #include <cmath>
@@ -23,7 +24,8 @@ static void pose_at(double yaw, double x, double y, double z, double T[12])
     T[9] = x; T[10] = y; T[11] = z;
 }
 
-static int build(svi_ba* ba, int n_kf, int n_lm, int track, std::mt19937_64& rng, bool imu)
+// fix_every > 0: every fix_every-th key frame is a fixed pose (fixed and free poses interleave in slot order)
+static int build(svi_ba* ba, int n_kf, int n_lm, int track, std::mt19937_64& rng, bool imu, int fix_every)
 {
     std::uniform_real_distribution<double> U(-1.0, 1.0);
     const double fx = 450.5, cx = 376.0, cy = 222.0, fb = 49.63;
@@ -44,7 +46,9 @@ static int build(svi_ba* ba, int n_kf, int n_lm, int track, std::mt19937_64& rng
         CHECK(svi_ba_add_landmark(ba, l, pw, 0));
     }
     for (int k = 0; k < n_kf; ++k) {
-        if (k > 0) {
+        if (k > 0 && fix_every > 0 && k % fix_every == 0) {
+            CHECK(svi_ba_add_pose(ba, 1000000 + k, &T[(size_t)12 * k], 1));
+        } else if (k > 0) {
             const double a[3] = {0.1 * U(rng), 0.1 * U(rng), -0.99};
             CHECK(svi_ba_add_keyframe(ba, 1000000 + k, 1000000 + k - 1, &T[(size_t)12 * k], nullptr, imu ? a : nullptr));
         }
@@ -89,7 +93,7 @@ int main(int argc, char** argv)
             svi_ba* ba = nullptr;
             CHECK(svi_ba_create(&o, &ba));
             std::mt19937_64 g2(seed * 7919 + gi); // the same graph on every rank
-            if (build(ba, n_kf, n_lm, track, g2, gi % 2 == 1)) return 1;
+            if (build(ba, n_kf, n_lm, track, g2, gi % 2 == 1, gi % 4 == 3 ? 7 : 0)) return 1;
             CHECK(svi_ba_initialize(ba));
             svi_ba_stats st;
             CHECK(svi_ba_get_stats(ba, &st));
